@@ -11,6 +11,11 @@ fused AdamW, grad clip 1.0, data parallel over RCCL (native bucketed reducer; --
 on the box).  A "step" is one full optimizer step (all micro-batches + all-reduce + clip + AdamW).
 W untimed warmup steps, then exactly K steps between barrier+synchronize pairs; the MAX elapsed
 over ranks is reported; rank 0 prints one JSON line.
+
+A plain run does only that.  ``--full`` adds the measurements that take runs of their own (the post-timing
+all-reduce bandwidth probe of a multi-rank job).  ``--dump-outputs DIR`` writes what the last timed step left its
+caller (loss, gradient norm, seeded samples of the gradients and of the updated parameters) as DIR/<name>.npy;
+model init and token stream are seeded, so two runs with the same arguments see identical inputs.
 """
 import argparse
 import json
@@ -74,6 +79,35 @@ def _allreduce_probe(dev: str, world: int, bucket_mb: float, iters: int = 10) ->
     return out
 
 
+DUMP_SAMPLE = 4096  # elements kept per parameter tensor: 2 x 4 MB of fp32 for the 280M models, far below 64 MB
+
+
+def _dump_outputs(path: str, model, loss: torch.Tensor, norm: torch.Tensor) -> None:
+    """The last timed step's results as float32 .npy files: its loss and (averaged, pre-clip) gradient norm, and a
+    fixed seeded sample (every element of a tensor of up to DUMP_SAMPLE elements) of each parameter's accumulated
+    gradient and of its value after the optimizer update, concatenated in ``model.parameters()`` order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(20240229)
+    params, grads = [], []
+    for p in model.parameters():
+        n = p.numel()
+        idx = None
+        if n > DUMP_SAMPLE:
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=gen).to(p.device)
+        for t, dst in ((p.detach(), params), (p.grad, grads)):
+            if t is None:
+                continue
+            flat = t.detach().reshape(-1)
+            dst.append((flat if idx is None else flat[idx]).float().cpu())
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "grad_norm.npy"), norm.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "params_sample.npy"), torch.cat(params).numpy())
+    if grads:
+        np.save(os.path.join(path, "grads_sample.npy"), torch.cat(grads).numpy())
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -102,6 +136,12 @@ def main():
                    help="recompute every N-th block in the backward (memory for long sequences; 0 = off)")
     p.add_argument("--dp-impl", default="native", choices=["native", "ddp"],
                    help="gradient all-reduce: native bucketed reducer (parallel/reducer.py) or torch DDP")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beside the headline figure (multi-rank: the all-reduce "
+                        "bandwidth probe after the timed steps); off: set up, warm up, time the steps, report")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the last step's loss, gradient norm and seeded samples of "
+                        "the gradients and updated parameters to DIR/<name>.npy (float32)")
     a = p.parse_args()
     if a.gpus > 1 and "RANK" not in os.environ:
         sys.exit(_relaunch_under_torchrun(sys.argv[1:], a.gpus))
@@ -169,7 +209,7 @@ def main():
         norm = ddp_mod.clip_and_step(dmodel, opt, 1.0)
         if a.trace_loss and info.master:
             print(f"step loss {loss_acc.item():.5f} grad_norm {norm.item():.4f}", flush=True)
-        return loss_acc
+        return loss_acc, norm
 
     red = ddp_mod._reducer(dmodel)
     for _ in range(a.warmup):
@@ -181,14 +221,14 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        last = step()
+        last, last_norm = step()
     barrier()
     sync()
     elapsed = torch.tensor(time.perf_counter() - t0, device=dev, dtype=torch.float64)
     all_reduce_max(elapsed)
     elapsed = float(elapsed.item())
     comm_probe = {}
-    if world > 1:
+    if world > 1 and a.full:
         # after the timed region: the gradient all-reduce's bus bandwidth at the bucket size over this job's RCCL
         # rings (xGMI on one node), rccl-tests convention busbw = 2 (n - 1) / n x bytes / t
         comm_probe = _allreduce_probe(dev, world, a.bucket_cap_mb)
@@ -210,6 +250,8 @@ def main():
     # the run is memory-bound on the allocator, not on the kernels
     alloc_retries = int(torch.cuda.memory_stats().get("num_alloc_retries", 0)) if dev.startswith("cuda") else 0
     loss_v = float(last.item())
+    if a.dump_outputs and info.master:
+        _dump_outputs(a.dump_outputs, ddp_mod.unwrap(dmodel), last, torch.as_tensor(last_norm))
     if a.profile_steps and info.master:
         from torch.profiler import ProfilerActivity, profile
         with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:

@@ -146,7 +146,7 @@ def test_bench_multi_rank_flow_on_cpu(dp_impl):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--model", "mamba2-tiny", "--B", "2", "--T", "64", "--global-batch-tokens", "512",
-           "--steps", "2", "--warmup", "1", "--dp-impl", dp_impl]
+           "--steps", "2", "--warmup", "1", "--dp-impl", dp_impl, "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=_env(), timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -176,6 +176,41 @@ def test_bench_gpus2_relaunches_under_torchrun():
     assert out["n_gpus"] == 2 and out["config"]["parallelism"] == "dp2"
     assert out["config"]["comm"]["world_size"] == 2 and out["config"]["comm"]["n_buckets"] >= 1
     assert out["config"]["grad_accum"] == 2
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """``bench.py --dump-outputs DIR`` on CPU with the tiny model: float32 .npy files of the last timed step's
+    results, identical from run to run (seeded init and tokens), and ``--steps`` sets the timed steps (one more
+    step moves the parameters)."""
+    import json
+    import numpy as np
+
+    def run(name, steps):
+        d = tmp_path / name
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+               "--model", "mamba2-tiny", "--B", "2", "--T", "32", "--global-batch-tokens", "128",
+               "--dump-outputs", str(d)]
+        env = {k: v for k, v in _env().items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+        env["CUDA_VISIBLE_DEVICES"] = env["HIP_VISIBLE_DEVICES"] = ""  # the CPU path, on a GPU machine too
+        p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == steps and out["ms_per_step"] > 0
+        assert "allreduce_100MB_ms" not in out["config"]["comm"]
+        arrs = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert set(arrs) == {"loss", "grad_norm", "params_sample", "grads_sample"}, sorted(arrs)
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in arrs.values())
+        assert sum(v.nbytes for v in arrs.values()) <= 64 * 2**20
+        assert abs(float(arrs["loss"][0]) - out["config"]["final_loss"]) <= 1e-4
+        return arrs
+
+    a, b, c = run("a", 2), run("b", 2), run("c", 3)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert a["params_sample"].shape == c["params_sample"].shape
+    assert not np.array_equal(a["params_sample"], c["params_sample"])
 
 
 def test_bench_refuses_world_mismatch():
